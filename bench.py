@@ -5,6 +5,7 @@ per-GPU batch 256 (BASELINE.json configs[1]); weak scaling over GPUs with RCCL g
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --gpus N ...                      (starts its own N ranks: parallel.ensure_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (same job; N must match)
+    python bench.py ... --dump-outputs DIR            (also writes what the last timed step computed: DIR/<name>.npy)
 
 Prints ONE JSON line (rank 0).  `value` is whole-job images/sec with inputs resident in HBM.
 `roofline` is measured live with HIP events on the launch stream in an extra instrumented step
@@ -30,6 +31,7 @@ MFMA_BF16_PEAK = 2.5e15   # dense bf16 MFMA, /opt/skills/guides/MI355X_MICROARCH
 HBM_PEAK = 8.0e12         # HBM3E spec, same guide (6.29 TB/s measured copy)
 WGRAD_STREAM_DEFAULT = "1"   # +2.2 % same-box (16.29k -> 16.65k img/s); HC_WGRAD_STREAM=0 switches it off
 TRAIN_GFLOP_PER_IMG = 16.88  # conv fwd+dgrad+wgrad (stem dgrad excluded), 2*MAC
+DUMP_SAMPLE = 1 << 22        # --dump-outputs: elements kept of the flattened parameters and of the gradients (16 MB each in fp32)
 
 
 def parse():
@@ -55,6 +57,13 @@ def parse():
     ap.add_argument("--loss-tail", type=int, default=0,
                     help="after the timed region run this many more steps and report each one's loss (config.loss_tail): the loss "
                          "trajectory of two runs with the same flags must agree bit for bit under --deterministic")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region write what its last step computed as DIR/<name>.npy (float32): loss, logits, "
+                         "BatchNorm running statistics and a fixed seeded sample of the updated parameters and of their gradients.  "
+                         "Implies --deterministic, so that two runs with the same arguments compute and write the same bits: the "
+                         "default step's reductions round in arrival order, and even one step from the same state then differs by "
+                         "~2e-2 in the logits and ~0.5 in the gradients (rel. L2, bf16 rounding flips); the result line then reports "
+                         "the deterministic step's time")
     ap.add_argument("--comm-dtype", choices=["fp32", "bf16"], default="fp32",
                     help="dtype of the gradient all-reduce at N > 1 (fp32 = the reference's gradient precision; bf16 halves the "
                          "bytes on xGMI but moves an AdaBelief update by ~2e-2, tests/test_parallel_gloo.py)")
@@ -95,6 +104,27 @@ def cpu_baseline(batch, iters):
             "threads_tried": {str(k): round(v, 2) for k, v in trial.items()},
             "sample": f"oracle (torch-CPU fp32 restatement of the reference) repvgg_a0 train step, batch {batch}, "
                       f"1 warm-up + {iters} timed iterations on the best of the tried thread counts"}
+
+
+def dump_outputs(out_dir, model, loss, logits):
+    """What the last timed step hands its caller, as float32 arrays: ``loss`` (1,), ``logits`` (batch, classes), ``bn_running_stats``
+    (the running_mean / running_var buffers in named_buffers order), and ``params`` / ``grads``: the updated parameters and their
+    gradients (zeros for a parameter without one) flattened in named_parameters order, sampled at DUMP_SAMPLE fixed positions (seed 0,
+    ascending) when longer."""
+    import numpy as np
+    params = [p for _, p in model.named_parameters()]
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+    if flat_p.numel() > DUMP_SAMPLE:
+        idx = torch.randperm(flat_p.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+        idx = idx.to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    stats = torch.cat([b.detach().reshape(-1).float() for n, b in model.named_buffers() if n.endswith(("running_mean", "running_var"))])
+    arrays = {"loss": loss.detach().float().reshape(1), "logits": logits.detach().float(), "bn_running_stats": stats,
+              "params": flat_p, "grads": flat_g}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 SECONDARY = [   # (key, BASELINE.json config, script under scripts/, extra arguments)
@@ -138,6 +168,8 @@ def run_secondary(steps, timeout_s=420):
 
 def main():
     args = parse()
+    if args.dump_outputs:
+        args.deterministic = True
     # `bench.py --gpus N` IS the N-rank job: with no launcher around it this process starts the N ranks itself (one per GPU) and
     # exits with their status; under torchrun WORLD_SIZE must equal --gpus (a mismatch is a mis-launch, not a 1-GPU measurement)
     from holocron_amd.parallel import ensure_ranks
@@ -215,10 +247,15 @@ def main():
     x = torch.rand((args.batch, 3, 224, 224), device=dev, generator=g)
     t = torch.randint(0, 10, (args.batch,), device=dev, generator=g)
     loss_buf = torch.zeros((), device=dev)
+    # --dump-outputs: the logits are copied out like the loss (holding the step's own tensor would keep its autograd graph alive
+    # into the next step and its capture)
+    logits_buf = torch.zeros((args.batch, 10), device=dev) if args.dump_outputs else None
 
     def seg_fwd_bwd():
         opt.zero_grad(set_to_none=True)
         logits = model(x)
+        if logits_buf is not None:
+            logits_buf.copy_(logits.detach())
         # the criterion of references/classification/train.py:194 as two HIP launches (torch composes it from ~25 small kernels);
         loss = h.nn.functional.cross_entropy(logits, t, label_smoothing=0.1)
         loss.backward()
@@ -306,6 +343,8 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:      # before anything else runs a step: the loss tail and the roofline's steps train on
+        dump_outputs(args.dump_outputs, model, loss_buf, logits_buf)
     final_loss = float(loss_buf.item())
     loss_tail = []
     for _ in range(args.loss_tail):          # untimed: every rank runs them (they hold collectives at N > 1)
@@ -410,7 +449,8 @@ def main():
                                f"{args.arch} bf16 train step (fwd+bwd+AdaBelief), synthetic 224^2, bs={args.batch} per MI355X (side measurement, "
                                "not a BASELINE config), random-init weights, 10 classes, CE label_smoothing 0.1",
                    "global_batch": args.batch * world, "parallelism": f"dp{world}", "mode": graph_note,
-                   "final_loss": final_loss, **({"loss_tail": loss_tail, "deterministic": bool(args.deterministic)} if loss_tail else {})},
+                   "final_loss": final_loss, **({"dump_outputs": args.dump_outputs, "deterministic": True} if args.dump_outputs else {}),
+                   **({"loss_tail": loss_tail, "deterministic": bool(args.deterministic)} if loss_tail else {})},
         "mfma_fraction_whole_step": (TRAIN_GFLOP_PER_IMG * 1e9 * imgs / dt / MFMA_BF16_PEAK / world) if headline else None,
         "conv_mfma_fraction": conv_frac,
         "roofline": roof,

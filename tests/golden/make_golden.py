@@ -750,6 +750,28 @@ def gen_mixup():
     save("mixup.pt", out)
 
 
+def gen_trainer():
+    """The trainer surface of the reference for tests/test_boundary_api.py: the parameter names of every method the Trainer class
+    defines (trainer/core.py), and what freeze_model / split_normalization_params (trainer/utils.py) do to the tiny net of
+    tests/_inputs.py."""
+    import importlib
+    import inspect
+    from _inputs import tiny_net
+    core = importlib.import_module("ref_holocron.trainer.core")
+    utils = importlib.import_module("ref_holocron.trainer.utils")
+    methods = {n: [a.name for a in inspect.signature(getattr(core.Trainer, n)).parameters.values() if a.kind == a.POSITIONAL_OR_KEYWORD]
+               for n, v in vars(core.Trainer).items() if inspect.isfunction(v) or isinstance(v, staticmethod)}
+    freeze = []
+    for layer in (None, "0", "1", "5"):
+        m = tiny_net()
+        utils.freeze_model(m, layer)
+        norm, other = utils.split_normalization_params(m)
+        freeze.append({"layer": layer, "requires_grad": [p.requires_grad for p in m.parameters()],
+                       "training": [mod.training for mod in m.modules()],
+                       "norm_shapes": [tuple(p.shape) for p in norm], "other_shapes": [tuple(p.shape) for p in other]})
+    save("trainer.pt", {"methods": methods, "freeze": freeze})
+
+
 def gen_nms():
     """torchvision.ops.nms is absent: these vectors come from the restated algorithm (oracle/tv_ops.py),
     plus the two situations the reference's own tests pin (tests/test_models_detection.py:158-163: disjoint
@@ -804,6 +826,6 @@ def gen_whole_models():
 
 if __name__ == "__main__":
     gens = {"whole_models": gen_whole_models, "boxes": gen_boxes, "functional": gen_functional, "optim": gen_optim, "repblock": gen_repblock,
-            "repvgg_small": gen_repvgg_small, "darknet": gen_darknet, "losses": gen_losses, "yolo": gen_yolo, "rexnet": gen_rexnet, "convs": gen_convs, "optim2": gen_optim2, "nms": gen_nms, "mobileone": gen_mobileone, "optim3": gen_optim3, "yolo_v1": gen_yolo_v1, "mixup": gen_mixup}
+            "repvgg_small": gen_repvgg_small, "darknet": gen_darknet, "losses": gen_losses, "yolo": gen_yolo, "rexnet": gen_rexnet, "convs": gen_convs, "optim2": gen_optim2, "nms": gen_nms, "mobileone": gen_mobileone, "optim3": gen_optim3, "yolo_v1": gen_yolo_v1, "mixup": gen_mixup, "trainer": gen_trainer}
     for name in (sys.argv[1:] or list(gens)):
         gens[name]()

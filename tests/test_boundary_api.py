@@ -8,8 +8,9 @@ import sys
 import pytest
 import torch
 
+from _inputs import tiny_net
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 
 def test_script_import_lists_resolve_through_the_alias():
@@ -49,9 +50,8 @@ def test_script_import_lists_resolve_through_the_alias():
     assert all(callable(f) for f in (freeze_bn, freeze_model, split_normalization_params))
 
 
-def test_trainer_signature_matches_reference():
-    """constructor and method names / parameters of trainer/core.py:26-104,277-451 (checked against the reference source when it
-    is available in this container)"""
+def test_trainer_signature_matches_reference(golden):
+    """constructor and method names / parameters of trainer/core.py:26-104,277-451 (the reference's own lists: tests/golden/trainer.pt)"""
     from holocron_amd.trainer import Trainer
     want = ["self", "model", "train_loader", "val_loader", "criterion", "optimizer", "gpu", "output_file", "amp", "skip_nan_loss",
             "nan_tolerance", "gradient_acc", "gradient_clip", "on_epoch_end"]
@@ -63,24 +63,16 @@ def test_trainer_signature_matches_reference():
         assert callable(getattr(Trainer, name)), name
     assert list(inspect.signature(Trainer.fit_n_epochs).parameters)[:6] == ["self", "num_epochs", "lr", "freeze_until", "sched_type",
                                                                             "norm_weight_decay"]
-    if os.path.exists(os.path.join(REF, "holocron", "trainer", "core.py")):
-        import ast
-        tree = ast.parse(open(os.path.join(REF, "holocron", "trainer", "core.py")).read())
-        cls = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "Trainer"][0]
-        for fn in [n for n in cls.body if isinstance(n, ast.FunctionDef)]:
-            ours = getattr(Trainer, fn.name, None)
-            assert ours is not None, fn.name
-            ref_args = [a.arg for a in fn.args.args]
-            our_args = list(inspect.signature(ours).parameters)
-            if isinstance(inspect.getattr_static(Trainer, fn.name), staticmethod):
-                ref_args = [a for a in ref_args if a != "self"]
-            assert our_args[:len(ref_args)] == ref_args, (fn.name, our_args, ref_args)
+    for name, ref_args in golden("trainer.pt")["methods"].items():
+        ours = getattr(Trainer, name, None)
+        assert ours is not None, name
+        our_args = list(inspect.signature(ours).parameters)
+        if isinstance(inspect.getattr_static(Trainer, name), staticmethod):
+            ref_args = [a for a in ref_args if a != "self"]
+        assert our_args[:len(ref_args)] == ref_args, (name, our_args, ref_args)
 
 
-def _tiny():
-    torch.manual_seed(0)
-    return torch.nn.Sequential(torch.nn.Conv2d(3, 4, 3, padding=1), torch.nn.BatchNorm2d(4), torch.nn.ReLU(),
-                               torch.nn.AdaptiveAvgPool2d(1), torch.nn.Flatten(), torch.nn.Linear(4, 6))
+_tiny = tiny_net
 
 
 def test_freeze_helpers():
@@ -105,23 +97,17 @@ def test_freeze_helpers():
     assert not m2[1].training and m2[0].training
 
 
-def test_helpers_match_reference_when_available():
-    if not os.path.exists(os.path.join(REF, "holocron", "trainer", "utils.py")):
-        pytest.skip("reference tree not present")
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("ref_trainer_utils", os.path.join(REF, "holocron", "trainer", "utils.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+def test_helpers_match_reference_when_available(golden):
+    """freeze_model / split_normalization_params against what the reference's trainer/utils.py does to the same net
+    (tests/golden/trainer.pt)"""
     from holocron_amd.trainer import utils as ours
-    for layer in (None, "0", "1", "5"):
-        a, b = _tiny(), _tiny()
-        ours.freeze_model(a, layer)
-        ref.freeze_model(b, layer)
-        assert [p.requires_grad for p in a.parameters()] == [p.requires_grad for p in b.parameters()]
-        assert [m.training for m in a.modules()] == [m.training for m in b.modules()]
+    for c in golden("trainer.pt")["freeze"]:
+        a = _tiny()
+        ours.freeze_model(a, c["layer"])
+        assert [p.requires_grad for p in a.parameters()] == c["requires_grad"]
+        assert [m.training for m in a.modules()] == c["training"]
         na, oa = ours.split_normalization_params(a)
-        nb, ob = ref.split_normalization_params(b)
-        assert [tuple(p.shape) for p in na] == [tuple(p.shape) for p in nb] and [tuple(p.shape) for p in oa] == [tuple(p.shape) for p in ob]
+        assert [tuple(p.shape) for p in na] == c["norm_shapes"] and [tuple(p.shape) for p in oa] == c["other_shapes"]
 
 
 def test_classification_trainer_cpu_loop(tmp_path):
@@ -178,22 +164,21 @@ def test_detection_assign_iou_and_metrics():
     assert sorted(zip(gi, pi)) == [(0, 0), (1, 1)]          # gt 2 also prefers pred 0 but gt 0 has the higher IoU
     s = DetectionTrainer._eval_metrics_str({"loc_err": 0.25, "clf_err": None, "det_err": 0.5})
     assert "25.00%" in s and "N/A" in s
-    if os.path.exists(os.path.join(REF, "holocron", "trainer", "detection.py")):
-        sys.path.insert(0, ROOT)
-        from oracle import tv_ops
-        torch.manual_seed(0)
-        for _ in range(5):
-            a = torch.rand(7, 4) * 50
-            a[:, 2:] += a[:, :2] + 1
-            b = a[torch.randperm(7)[:5]] + torch.rand(5, 4)
-            b = torch.cat([b, b[:2] + 0.3])                  # duplicates: several ground truths compete for one prediction
-            iou = tv_ops.box_iou(a, b).max(dim=1)
-            kept = iou.values >= 0.5
-            gi, pi = assign_iou(a, b, 0.5)
-            assert len(set(pi)) == len(pi) and all(bool(kept[g]) for g in gi)
-            for g_, p_ in zip(gi, pi):                       # each chosen pair is the best ground truth of its prediction
-                rivals = [float(iou.values[k]) for k in range(a.shape[0]) if bool(kept[k]) and int(iou.indices[k]) == p_]
-                assert abs(float(iou.values[g_]) - max(rivals)) < 1e-6
+    sys.path.insert(0, ROOT)
+    from oracle import tv_ops
+    torch.manual_seed(0)
+    for _ in range(5):
+        a = torch.rand(7, 4) * 50
+        a[:, 2:] += a[:, :2] + 1
+        b = a[torch.randperm(7)[:5]] + torch.rand(5, 4)
+        b = torch.cat([b, b[:2] + 0.3])                  # duplicates: several ground truths compete for one prediction
+        iou = tv_ops.box_iou(a, b).max(dim=1)
+        kept = iou.values >= 0.5
+        gi, pi = assign_iou(a, b, 0.5)
+        assert len(set(pi)) == len(pi) and all(bool(kept[g]) for g in gi)
+        for g_, p_ in zip(gi, pi):                       # each chosen pair is the best ground truth of its prediction
+            rivals = [float(iou.values[k]) for k in range(a.shape[0]) if bool(kept[k]) and int(iou.indices[k]) == p_]
+            assert abs(float(iou.values[g_]) - max(rivals)) < 1e-6
 
 
 def test_transforms_resize_and_zoom_out():

@@ -40,3 +40,21 @@ def test_forced_dist_bench_step_matches_the_single_graph_step_bit_for_bit():
     assert len(a) == 5 and a == b, (a, b)
     assert single["config"]["final_loss"] == dist["config"]["final_loss"]
     assert a[-1] < a[0] + 1e-3                   # ... and it trains
+
+
+def test_dump_outputs_repeat_bit_for_bit(tmp_path):
+    """bench.py --dump-outputs: two runs with the same arguments write the same arrays (the flag implies the deterministic step)."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--profile-steps", "1",
+           "--no-cpu-baseline", "--no-secondary", "--batch", "64"]
+    for run in ("a", "b"):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(next(ln for ln in reversed(r.stdout.splitlines()) if ln.startswith("{")))
+        assert line["steps"] == 3 and line["config"]["deterministic"] is True
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["bn_running_stats.npy", "grads.npy", "logits.npy", "loss.npy", "params.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), n
+    assert np.load(tmp_path / "a" / "logits.npy").shape == (64, 10)

@@ -786,3 +786,36 @@ def test_gather_conv_accumulators_stay_in_registers(tmp_path):
     assert len(names) == len(scratch) and len(names) >= 20
     bad = [(n[:60], s) for n, s in zip(names, scratch) if "conv_gather_kernel" in n and s != "0"]
     assert not bad, bad
+
+
+def test_bench_dump_outputs_are_float32_bounded_and_aligned(tmp_path):
+    """bench.py --dump-outputs: float32 arrays within 64 MB for the headline model (24.7 M parameters, so the parameter and gradient
+    vectors are sampled), the sample positions fixed by the seed, the gradient sample taken at the parameter sample's positions (zeros
+    for a parameter without a gradient), and every running_mean / running_var buffer in named_buffers order.
+    A child process: importing bench.py sets its environment defaults."""
+    import subprocess
+    import sys
+    import numpy as np
+    import holocron_amd as h
+    code = ("import sys, torch; sys.path.insert(0, sys.argv[1]); import bench, holocron_amd as h\n"
+            "torch.manual_seed(0); m = h.models.repvgg_a0(num_classes=10)\n"
+            "for p in m.parameters(): p.grad = p.detach() * 2\n"
+            "m.head.bias.grad = None\n"
+            "bench.dump_outputs(sys.argv[2], m, torch.tensor(2.5), torch.randn(256, 10).to(torch.bfloat16))\n"
+            "print(bench.DUMP_SAMPLE)")
+    r = subprocess.run([sys.executable, "-c", code, ROOT, str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    n = int(r.stdout.split()[-1])
+    out = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(out) == {"loss", "logits", "bn_running_stats", "params", "grads"}
+    assert all(a.dtype == np.float32 for a in out.values())
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 << 20
+    assert out["loss"].tolist() == [2.5] and out["logits"].shape == (256, 10) and out["params"].shape == (n,)
+    torch.manual_seed(0)
+    m = h.models.repvgg_a0(num_classes=10)
+    flat = torch.cat([p.detach().reshape(-1) for p in m.parameters()])
+    grads = torch.cat([p.detach().reshape(-1) * (0 if p is m.head.bias else 2) for p in m.parameters()])
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+    assert np.array_equal(out["params"], flat[idx].numpy()) and np.array_equal(out["grads"], grads[idx].numpy())
+    stats = torch.cat([b.reshape(-1) for k, b in m.named_buffers() if k.endswith(("running_mean", "running_var"))])
+    assert out["bn_running_stats"].shape == (33632,) and np.array_equal(out["bn_running_stats"], stats.numpy())

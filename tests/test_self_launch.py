@@ -30,7 +30,9 @@ def test_gpus_1_without_launcher_runs_in_process():
 
 
 def test_gpus_2_without_launcher_starts_two_ranks():
-    r = subprocess.run([sys.executable, STUB, "--gpus", "2", "--steps", "3"], env=_env(), capture_output=True, text=True, timeout=600)
+    # CPU ranks whatever the host: with a GPU visible, ensure_ranks refuses more ranks than devices (a one-GPU host has too few)
+    env = _env(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, STUB, "--gpus", "2", "--steps", "3"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert _json_line(r.stdout) == {"n_gpus": 2, "steps": 3, "sum_of_ranks": 3.0}      # ranks 0 and 1 both took part: 1 + 2
 
