@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
+from _kernel_trace import launched_gather_form
 
 pytestmark = pytest.mark.gpu
 
@@ -20,18 +21,36 @@ def _to_nchw_f32(y):
     return y.float().cpu().contiguous()
 
 
+# conv_gather_kernel<MR, NR, WM, WN, BK, FP8, NS, MINB> instantiations (csrc/conv_gather.hip) the cases below reach; every form has its
+# own ragged cases in tests/test_gpu_conv_forms.py
+SHORT64 = (1, 2, 2, 2, 32, False, 2, 4)     # short-loop form, 64 x 128 tile
+SHORT128 = (2, 2, 2, 2, 32, False, 2, 4)    # short-loop form, 128 x 128 tile
+BIG256 = (4, 2, 2, 4, 32, False, 4, 1)      # big tile, 256 x 256
+BIG128 = (4, 2, 1, 8, 32, False, 4, 1)      # big tile, 128 x 512
+
 CONV_CASES = [
     # N, Cin, Cout, H, W, k, stride
-    (2, 16, 48, 13, 13, 3, 1),     # BK=16, 64-wide channel tile with padding
-    (2, 48, 48, 14, 9, 3, 2),
-    (3, 32, 96, 9, 9, 3, 1),       # BK=32, 96 tile
-    (2, 64, 192, 14, 14, 3, 1),    # BK=64, 192 tile
-    (2, 192, 192, 7, 7, 1, 1),
-    (2, 64, 128, 10, 10, 3, 2),    # 128 tile
-    (1, 128, 320, 7, 7, 3, 1),     # two channel tiles + ragged
-    (2, 96, 40, 5, 5, 1, 2),       # Cout % 32 != 0
-    (5, 16, 255, 6, 6, 1, 1),      # Cout % 4 != 0 (YOLO head width): scalar store path
+    (2, 16, 48, 13, 13, 3, 1),     # classic k16 steps, 64-channel tile with padding
+    (2, 48, 48, 14, 9, 3, 2),      # the same, stride 2
+    (3, 32, 96, 9, 9, 3, 1),       # taps x Cin <= 1152: short loop, 96 of 128 channel rows
+    (2, 64, 192, 14, 14, 3, 1),    # short loop, three 64-channel tiles
+    (2, 192, 192, 7, 7, 1, 1),     # classic k64 steps; few tiles: the fill rule's 64-channel tile
+    (2, 64, 128, 10, 10, 3, 2),    # short loop, stride 2
+    (1, 128, 320, 7, 7, 3, 1),     # short loop, five 64-channel tiles
+    (2, 96, 40, 5, 5, 1, 2),       # 1 x 1 over <= 128 channels: short loop; 40 of 64 channel rows
+    (5, 16, 255, 6, 6, 1, 1),      # Cout % 4 != 0 (YOLO head width): classic k16, scalar store path
 ]
+CONV_FORMS = {   # case -> instantiation it reaches
+    (2, 16, 48, 13, 13, 3, 1): (1, 2, 2, 2, 16, False, 2, 2),
+    (2, 48, 48, 14, 9, 3, 2): (1, 2, 2, 2, 16, False, 2, 2),
+    (3, 32, 96, 9, 9, 3, 1): SHORT128,
+    (2, 64, 192, 14, 14, 3, 1): SHORT64,
+    (2, 192, 192, 7, 7, 1, 1): (1, 2, 2, 2, 64, False, 2, 2),
+    (2, 64, 128, 10, 10, 3, 2): SHORT128,
+    (1, 128, 320, 7, 7, 3, 1): SHORT64,
+    (2, 96, 40, 5, 5, 1, 2): SHORT64,
+    (5, 16, 255, 6, 6, 1, 1): (2, 2, 2, 2, 16, False, 2, 2),
+}
 
 
 @pytest.mark.parametrize("N,Cin,Cout,H,W,k,stride", CONV_CASES)
@@ -44,7 +63,9 @@ def test_conv_forward_matches_cpu(N, Cin, Cout, H, W, k, stride):
     ref = F.conv2d(x, w, b, stride, k // 2)
     from holocron_amd import _lib
     stats = torch.zeros(_lib.stat_replicas(), 2, Cout, device="cuda")
-    out = cv.conv2d(x.cuda(), w.cuda(), b.cuda(), stride, k // 2, stats=stats)
+    res = []
+    assert launched_gather_form(lambda: res.append(cv.conv2d(x.cuda(), w.cuda(), b.cuda(), stride, k // 2, stats=stats))) == CONV_FORMS[(N, Cin, Cout, H, W, k, stride)]
+    out = res[0]
     assert out.shape == ref.shape
     assert rel_l2(_to_nchw_f32(out), ref) < 3e-3
     # the statistics epilogue sees the fp32 accumulators BEFORE bias/rounding
@@ -57,19 +78,29 @@ def test_conv_forward_matches_cpu(N, Cin, Cout, H, W, k, stride):
 
 
 BIG_TILE_CASES = [
-    # N, Cin, Cout, H, W: shapes the efficiency predicate of the big-tile family (csrc/conv_gather.hip: hc_conv_gather) sends to the
-    # eight-wave pipelined kernel - ragged last pixel tile, ragged last channel tile, the 128 x 512 tile, and a launch of several rounds
-    (90, 64, 480, 19, 19),     # 256 x 256 tiles, 2 channel tiles (the second 224 of 256 rows), 127 pixel tiles with a ragged last one
-    (31, 64, 112, 64, 64),     # 128 x 512 tiles, 112 of 128 channel rows, 248 tiles
-    (16, 128, 128, 76, 76),    # YOLOv4's 128 @ 76 x 76 at batch 16: 181 tiles of 128 x 512, ragged last tile
-    (40, 96, 256, 40, 41),     # 256 x 256, 257 tiles: one full round + one tile (efficiency 0.5: stays on the 128 x 128 form)
+    # N, Cin, Cout, H, W.  3 x 3 over at most 128 channels (taps x Cin <= 1152) takes the short-loop form, which the
+    # dispatcher asks BEFORE the big-tile predicate; the eight-wave big-tile kernels need more input channels
+    (64, 320, 448, 29, 17),     # 256 x 256 tiles: 123.25 pixel tiles, the second channel tile 192 of 256 rows (efficiency 0.84)
+    (40, 320, 120, 61, 53),     # 128 x 512 tiles: 252.6 pixel tiles, 120 of 128 channel rows
+    (90, 64, 480, 19, 19),      # short loop: 4 channel tiles (the last 96 of 128 rows), 254 pixel tiles with a ragged last one
+    (31, 64, 112, 64, 64),      # short loop: 112 of 128 channel rows
+    (16, 128, 128, 76, 76),     # YOLOv4's 128 @ 76 x 76 at batch 16 (taps x Cin = 1152): short loop, ragged last pixel tile
+    (40, 96, 256, 40, 41),      # short loop, 513 pixel tiles
 ]
+BIG_TILE_FORMS = {   # case -> instantiation it reaches
+    (64, 320, 448, 29, 17): BIG256,
+    (40, 320, 120, 61, 53): BIG128,
+    (90, 64, 480, 19, 19): SHORT128,
+    (31, 64, 112, 64, 64): SHORT128,
+    (16, 128, 128, 76, 76): SHORT128,
+    (40, 96, 256, 40, 41): SHORT128,
+}
 
 
 @pytest.mark.parametrize("N,Cin,Cout,H,W", BIG_TILE_CASES)
 def test_conv_forward_big_tile_family_matches_cpu(N, Cin, Cout, H, W):
-    """3x3 forward + statistics + bias + ReLU through cv.conv2d at sizes where the launch-efficiency predicate picks the big-tile family
-    (and one where it must not): against torch-CPU fp32 on bf16-representable operands, same bounds as the small cases."""
+    """3x3 forward + statistics + bias + ReLU through cv.conv2d at sizes that reach both big-tile kernels with ragged edges, and at
+    the sizes that go to the short-loop form: against torch-CPU fp32 on bf16-representable operands, same bounds as the small cases."""
     from holocron_amd import _lib
     from holocron_amd.ops import conv as cv
     torch.manual_seed(Cin + Cout + H)
@@ -78,7 +109,9 @@ def test_conv_forward_big_tile_family_matches_cpu(N, Cin, Cout, H, W):
     b = torch.randn(Cout)
     ref = F.conv2d(x, w, b, 1, 1)
     stats = torch.zeros(_lib.stat_replicas(), 2, Cout, device="cuda")
-    out = cv.conv2d(x.cuda(), w.cuda(), b.cuda(), 1, 1, stats=stats)
+    res = []
+    assert launched_gather_form(lambda: res.append(cv.conv2d(x.cuda(), w.cuda(), b.cuda(), 1, 1, stats=stats))) == BIG_TILE_FORMS[(N, Cin, Cout, H, W)]
+    out = res[0]
     assert rel_l2(_to_nchw_f32(out), ref) < 3e-3
     # element-wise too: a mis-addressed ragged tile would hide in a norm over 10^7 elements
     assert float((_to_nchw_f32(out) - ref).abs().max()) < 0.05 * float(ref.abs().max())

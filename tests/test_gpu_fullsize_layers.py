@@ -472,6 +472,7 @@ def test_streaming_pointwise_conv_vs_fp32_cpu(cfg):
     from holocron_amd import _lib
     from holocron_amd._lib import check, ptr, stream
     from holocron_amd.ops import conv as cv
+    from _kernel_trace import launched, pw_forms
     N, Ci, Co, H, W = cfg
     dev = torch.device("cuda:0")
     lib = _lib.load()
@@ -487,8 +488,10 @@ def test_streaming_pointwise_conv_vs_fp32_cpu(cfg):
         d = cv.fwd_desc(N, Ci, H, W, Co, 1, 1, 1, 0)
         d.src0, d.wpk, d.dst, d.stats = ptr(xg), ptr(wpk), ptr(y), ptr(stats)
         assert lib.hc_conv_pointwise_supported(C.byref(d)) == 1
-        check(lib.hc_conv_pointwise(C.byref(d), stream()), "hc_conv_pointwise")
-        torch.cuda.synchronize()
+        names = launched(lambda: check(lib.hc_conv_pointwise(C.byref(d), stream()), "hc_conv_pointwise"))
+        ks = Ci // 16
+        ks = 1 if ks <= 1 else 2 if ks <= 2 else 4 if ks <= 4 else 8
+        assert pw_forms(names) == [(ks, with_stats)], names
         e = rel_l2(nchw(y), c)
         assert e < TOL_BF16, (cfg, with_stats, e)
         if with_stats:
