@@ -6,11 +6,15 @@ per-GPU batch 256 (BASELINE.json configs[1]); weak scaling over GPUs with RCCL g
     python bench.py --gpus N ...                      (starts its own N ranks: parallel.ensure_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (same job; N must match)
     python bench.py ... --dump-outputs DIR            (also writes what the last timed step computed: DIR/<name>.npy)
+    python bench.py ... --full                        (also the side measurements below)
 
 Prints ONE JSON line (rank 0).  `value` is whole-job images/sec with inputs resident in HBM.
-`roofline` is measured live with HIP events on the launch stream in an extra instrumented step
-(not part of the timed region) for the dominant kernel family; `cpu_baseline` times the CPU oracle
-(the reference's algorithm restated in torch-CPU fp32) on a bounded sample.
+A plain run does only what that figure needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+With --full it then also measures, after the timed region: `roofline` / `conv_mfma_fraction`, live with
+HIP events on the launch stream in extra instrumented eager steps, for the dominant kernel family and
+the conv families; `cpu_baseline`, the CPU oracle (the reference's algorithm restated in torch-CPU fp32)
+on a bounded sample; `secondary`, the other single-GPU BASELINE configs.  Without --full the first two are
+null and the last two absent.
 """
 import argparse
 import json
@@ -39,18 +43,22 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="timed steps (default: ~2.5 s of GPU time)")
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--profile-steps", type=int, default=8, help="instrumented eager steps behind the roofline object (untimed)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the side measurements (roofline and conv MFMA fraction from instrumented "
+                         "steps, CPU baseline, secondary BASELINE configs); a plain run only sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--profile-steps", type=int, default=8, help="--full: instrumented eager steps behind the roofline object (untimed)")
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (BASELINE config: 256)")
     ap.add_argument("--arch", default="repvgg_a0", help="the headline is repvgg_a0 (BASELINE.json configs[1]); other RepVGG variants for "
                                                         "side measurements (their line says so and carries no MFMA fraction)")
     ap.add_argument("--no-graph", action="store_true", help="do not capture the step in a hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-batch", type=int, default=32)
-    ap.add_argument("--cpu-iters", type=int, default=3)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-batch", type=int, default=32, help="--full: batch of the CPU baseline")
+    ap.add_argument("--cpu-iters", type=int, default=3, help="--full: timed iterations of the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary BASELINE configs (C3 rexnet1_0x, C4 yolov4 train / eval, C5 repvgg_a2 fp8) that rank 0 "
-                         "runs after the headline's timed region at N = 1 and reports under `secondary`")
-    ap.add_argument("--secondary-steps", type=int, default=10)
+                    help="--full: skip the secondary BASELINE configs (C3 rexnet1_0x, C4 yolov4 train / eval, C5 repvgg_a2 fp8) that "
+                         "rank 0 runs after the headline's timed region at N = 1 and reports under `secondary`")
+    ap.add_argument("--secondary-steps", type=int, default=10, help="--full: timed steps of each secondary config")
     ap.add_argument("--deterministic", action="store_true",
                     help="bit-reproducible steps (holocron_amd.set_deterministic: single-writer statistics slots); for A/B checks of the "
                          "step's code paths, not for the headline number")
@@ -351,12 +359,13 @@ def main():
         run_step()
         loss_tail.append(float(loss_buf.item()))
 
-    # ---- roofline: instrumented eager step, HIP events on the launch stream -----------------------
+    # ---- --full: roofline, instrumented eager steps, HIP events on the launch stream ---------------
     roof = None
-    cv.set_wgrad_side_stream(False)
-    if reducer is not None:
-        reducer.set_overlap(False)   # the instrumented step below runs on rank 0 only: no collectives, no hooks
-    if rank == 0:
+    if args.full:
+        cv.set_wgrad_side_stream(False)
+        if reducer is not None:
+            reducer.set_overlap(False)   # the instrumented step below runs on rank 0 only: no collectives, no hooks
+    if args.full and rank == 0:
         nparam = sum(p.numel() for p in model.parameters())
         nprof = max(1, args.profile_steps)
         fam = {}
@@ -455,9 +464,9 @@ def main():
         "conv_mfma_fraction": conv_frac,
         "roofline": roof,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.cpu_iters)
-    if world == 1 and headline and not args.no_secondary and not force_dist:
+    if args.full and world == 1 and headline and not args.no_secondary and not force_dist:
         # release this process's device memory first: the secondary drivers are separate processes on the same GPU
         del gstep, model, opt, x
         torch.cuda.empty_cache()

@@ -8,7 +8,7 @@
 # Writes gpurun_out/pmc_mfma/mfma_util.txt (copy to profiles/).
 cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/pmc_mfma; mkdir -p $O; rm -rf $O/*
-CMD="${PMC_CMD:-python bench.py --no-graph --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 1}"
+CMD="${PMC_CMD:-python bench.py --full --no-graph --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 1}"
 timeout 500 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_ANY -d $O -o m --output-format csv -- $CMD > $O/run.log 2>&1
 python - "$O" "$CMD" <<'PY'
 import csv, glob, sys, collections

@@ -5,7 +5,7 @@
 # are in KiB.  Writes gpurun_out/pmc_step/traffic.json (copy to profiles/).
 cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/pmc_step; rm -rf gpurun_out/pmc_step/*
-CMD="python bench.py --no-graph --steps 2 --warmup 1 --no-cpu-baseline"
+CMD="python bench.py --full --no-graph --steps 2 --warmup 1 --no-cpu-baseline"
 timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmc_step -o f --output-format csv -- $CMD > gpurun_out/pmc_step/run_f.log 2>&1
 timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/pmc_step -o w --output-format csv -- $CMD > gpurun_out/pmc_step/run_w.log 2>&1
 python - <<'PY'
@@ -22,7 +22,7 @@ for f in sorted(glob.glob("gpurun_out/pmc_step/**/*counter_collection.csv", recu
             continue
         a = agg[(k, r["Counter_Name"])]
         a[0] += float(r["Counter_Value"]); a[1] += 1
-out = {"command": "rocprofv3 --kernel-trace --pmc {FETCH_SIZE|WRITE_SIZE} -- python bench.py --no-graph --steps 2 --warmup 1 --no-cpu-baseline",
+out = {"command": "rocprofv3 --kernel-trace --pmc {FETCH_SIZE|WRITE_SIZE} -- python bench.py --full --no-graph --steps 2 --warmup 1 --no-cpu-baseline",
        "note": "bytes per launch, averaged over every launch of the family (warm-up + timed steps); read = 2 x FETCH_SIZE KiB, write = WRITE_SIZE KiB"}
 for k in ("conv_gather", "conv_rows", "conv_small", "conv_wgrad", "bn_elementwise"):
     fr, fn = agg.get((k, "FETCH_SIZE"), [0, 0]); wr, wn = agg.get((k, "WRITE_SIZE"), [0, 0])

@@ -27,9 +27,9 @@ for agg, suffix in ((per, "kernel_stats.txt"), (grid, "kernel_stats_by_grid.txt"
 PY
 }
 # ---- headline
-timeout 600 python $R/bench.py > $O/bench.log 2>&1; grep '^{' $O/bench.log | tail -1 > $O/r01_final_bench.json
-timeout 500 rocprofv3 --kernel-trace --stats -d $O/t_head -o p --output-format csv -- python $R/bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline > $O/t_head.log 2>&1
-summ $O/t_head $O/r01_final "rocprofv3 --kernel-trace --stats -- python bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline  (MI355X; eager steps incl. warm-up + the instrumented roofline step)"
+timeout 600 python $R/bench.py --full > $O/bench.log 2>&1; grep '^{' $O/bench.log | tail -1 > $O/r01_final_bench.json
+timeout 500 rocprofv3 --kernel-trace --stats -d $O/t_head -o p --output-format csv -- python $R/bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline > $O/t_head.log 2>&1
+summ $O/t_head $O/r01_final "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline  (MI355X; eager steps incl. warm-up + the instrumented roofline step)"
 grep '^{' $O/t_head.log | tail -1 > $O/r01_final_bench_under_rocprof.json
 # ---- secondary configurations: bench line (graph replay where the script captures) + eager trace
 sec() {  # sec <tag> <script> "<bench args>" "<trace args or empty>"

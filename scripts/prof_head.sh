@@ -4,8 +4,8 @@
 P=${1:-r02}
 cd /tmp; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_head; mkdir -p $O
-timeout 500 rocprofv3 --kernel-trace --stats -d $O/t_head -o p --output-format csv -- python $R/bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline > $O/t_head.log 2>&1
-python - "$O/t_head" "$O/$P" "rocprofv3 --kernel-trace --stats -- python bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline  (MI355X; eager steps incl. warm-up + the instrumented roofline step)" <<'PY'
+timeout 500 rocprofv3 --kernel-trace --stats -d $O/t_head -o p --output-format csv -- python $R/bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline > $O/t_head.log 2>&1
+python - "$O/t_head" "$O/$P" "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline  (MI355X; eager steps incl. warm-up + the instrumented roofline step)" <<'PY'
 import csv, glob, sys, collections
 d, out, header = sys.argv[1], sys.argv[2], sys.argv[3]
 f = glob.glob(d + "/**/*kernel_trace.csv", recursive=True)[0]

@@ -29,11 +29,11 @@ for agg, suffix, top in ((per, "kernel_stats.txt", 60), (grid, "kernel_stats_by_
 PY
 }
 # ---- headline
-timeout 900 python $R/bench.py > $O/bench.log 2>&1; grep '^{' $O/bench.log | tail -1 > $O/${P}_bench.json
-timeout 500 rocprofv3 --kernel-trace --stats -d $O/t_head -o p --output-format csv -- python $R/bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline > $O/t_head.log 2>&1
-summ $O/t_head $O/$P "rocprofv3 --kernel-trace --stats -- python bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline  (MI355X; eager steps incl. warm-up + the instrumented roofline step)"
+timeout 900 python $R/bench.py --full > $O/bench.log 2>&1; grep '^{' $O/bench.log | tail -1 > $O/${P}_bench.json
+timeout 500 rocprofv3 --kernel-trace --stats -d $O/t_head -o p --output-format csv -- python $R/bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline > $O/t_head.log 2>&1
+summ $O/t_head $O/$P "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline  (MI355X; eager steps incl. warm-up + the instrumented roofline step)"
 grep '^{' $O/t_head.log | tail -1 > $O/${P}_bench_under_rocprof.json
-HC_FORCE_DIST=1 timeout 300 python $R/bench.py --no-cpu-baseline > $O/dist.log 2>&1; grep '^{' $O/dist.log | tail -1 > $O/${P}_bench_forced_dist.json
+HC_FORCE_DIST=1 timeout 300 python $R/bench.py --full --no-cpu-baseline > $O/dist.log 2>&1; grep '^{' $O/dist.log | tail -1 > $O/${P}_bench_forced_dist.json
 # ---- secondary configurations: bench line + eager trace
 sec() {  # sec <tag> <script> "<bench args>" "<trace args or empty>"
   timeout 600 python $R/scripts/$2 $3 > $O/$1.log 2>&1; grep '^{' $O/$1.log | tail -1 > $O/${P}_$1_bench.json

@@ -31,12 +31,12 @@ trace() {  # trace <tag> <header> <command ...>
   summ $O/t_$tag $O/r03_final_$tag "$hdr"; rm -rf $O/t_$tag
 }
 # ---- headline: PMC traffic + MFMA utilisation, then the bench line, then the eager kernel trace
-bash scripts/pmc_families.sh step python bench.py --no-graph --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 1 > $O/pmc_step.log 2>&1
+bash scripts/pmc_families.sh step python bench.py --full --no-graph --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 1 > $O/pmc_step.log 2>&1
 cp gpurun_out/pmc_step/traffic.json profiles/r03_pmc_step_traffic.json; cp gpurun_out/pmc_step/traffic.json $O/r03_pmc_step_traffic.json
 bash scripts/pmc_mfma.sh > $O/pmc_mfma.log 2>&1; cp gpurun_out/pmc_mfma/mfma_util.txt $O/r03_mfma_util.txt
-timeout 600 python bench.py > $O/r03_final_bench.json 2> $O/bench.err
-HC_FORCE_DIST=1 timeout 300 python bench.py --no-cpu-baseline > $O/r03_final_bench_forced_dist.json 2> $O/bench_dist.err
-trace headline "rocprofv3 --kernel-trace --stats -- python bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1  (MI355X; eager steps incl. warm-up + one instrumented step)" python $R/bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1
+timeout 600 python bench.py --full > $O/r03_final_bench.json 2> $O/bench.err
+HC_FORCE_DIST=1 timeout 300 python bench.py --full --no-cpu-baseline > $O/r03_final_bench_forced_dist.json 2> $O/bench_dist.err
+trace headline "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1  (MI355X; eager steps incl. warm-up + one instrumented step)" python $R/bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1
 timeout 120 python scripts/bench_ew.py 2>&1 | grep -v amdgpu > $O/r03_final_bn_passes.txt
 timeout 200 python scripts/bench_s2.py 2>&1 | grep -v amdgpu > $O/r03_final_conv_s2_shapes.txt
 timeout 120 python scripts/check_rows.py 2>&1 | grep -v amdgpu > $O/r03_final_conv_rows_shapes.txt

@@ -36,16 +36,16 @@ trace() {  # trace <tag> <header> <command ...>
 }
 # ---- headline: PMC traffic + MFMA utilisation, then the bench line, then the eager kernel trace
 if want headline; then
-bash scripts/pmc_families.sh step python bench.py --no-graph --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 1 > $O/pmc_step.log 2>&1
+bash scripts/pmc_families.sh step python bench.py --full --no-graph --steps 2 --warmup 1 --no-cpu-baseline --profile-steps 1 > $O/pmc_step.log 2>&1
 cp gpurun_out/pmc_step/traffic.json profiles/r06_pmc_step_traffic.json; cp gpurun_out/pmc_step/traffic.json $O/r06_pmc_step_traffic.json
 bash scripts/pmc_mfma.sh > $O/pmc_mfma.log 2>&1; cp gpurun_out/pmc_mfma/mfma_util.txt $O/r06_mfma_util.txt
-timeout 600 python bench.py > $O/r06_final_bench.json 2> $O/bench.err
-HC_FORCE_DIST=1 timeout 300 python bench.py --no-cpu-baseline > $O/r06_final_bench_forced_dist.json 2> $O/bench_dist.err
+timeout 600 python bench.py --full > $O/r06_final_bench.json 2> $O/bench.err
+HC_FORCE_DIST=1 timeout 300 python bench.py --full --no-cpu-baseline > $O/r06_final_bench_forced_dist.json 2> $O/bench_dist.err
 # two eager kernel traces of the headline: SERIALISED (everything on one stream: per-kernel durations are the kernels' own) and
 # CONCURRENT (bench.py's default: finished weight-gradient groups on a second stream - durations of kernels that ran beside them are
 # inflated, the file says so in its header)
-HC_WREP_SIDE=0 HC_WGRAD_STREAM=0 trace headline_serialised "SERIALISED: HC_WREP_SIDE=0 HC_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- python bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1  (MI355X; one stream: per-kernel durations are undisturbed)" python $R/bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1
-trace headline_concurrent "CONCURRENT (weight gradients on a second stream, bench.py's default): rocprofv3 --kernel-trace --stats -- python bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1  (MI355X; durations of kernels that overlap the side stream are inflated - use the serialised file for per-kernel numbers)" python $R/bench.py --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1
+HC_WREP_SIDE=0 HC_WGRAD_STREAM=0 trace headline_serialised "SERIALISED: HC_WREP_SIDE=0 HC_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1  (MI355X; one stream: per-kernel durations are undisturbed)" python $R/bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1
+trace headline_concurrent "CONCURRENT (weight gradients on a second stream, bench.py's default): rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1  (MI355X; durations of kernels that overlap the side stream are inflated - use the serialised file for per-kernel numbers)" python $R/bench.py --full --steps 12 --warmup 3 --no-graph --no-cpu-baseline --profile-steps 1
 timeout 200 python scripts/bench_stem.py 2>&1 | grep -v amdgpu > $O/r06_final_stem_fused.txt
 ( for e in "HC_WGRAD_KNOCKOUT=0" "HC_WGRAD_KNOCKOUT=1" "HC_WGRAD_STREAM=0 HC_WREP_SIDE=0" "HC_STEM_FUSED=0"; do env $e timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('$e', round(d['ms_per_step'],3), 'ms/step')"; done ) > $O/r06_final_step_knockouts.txt
 timeout 120 python scripts/bench_ew.py 2>&1 | grep -v amdgpu > $O/r06_final_bn_passes.txt

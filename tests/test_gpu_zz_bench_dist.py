@@ -42,6 +42,23 @@ def test_forced_dist_bench_step_matches_the_single_graph_step_bit_for_bit():
     assert a[-1] < a[0] + 1e-3                   # ... and it trains
 
 
+def test_side_measurements_run_only_under_full():
+    """A plain run prints the headline line and nothing it needs extra steps or processes for; --full adds the instrumented roofline
+    steps (the CPU baseline and the secondary configs, skipped here for time, go behind the same flag)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "64"]
+    lines = []
+    for extra in ([], ["--full", "--profile-steps", "1", "--no-cpu-baseline", "--no-secondary"]):
+        r = subprocess.run(cmd + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(next(ln for ln in reversed(r.stdout.splitlines()) if ln.startswith("{"))))
+    plain, full = lines
+    for line in lines:
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert plain["roofline"] is None and plain["conv_mfma_fraction"] is None
+    assert "cpu_baseline" not in plain and "secondary" not in plain
+    assert full["roofline"]["instrumented_steps"] == 1 and full["conv_mfma_fraction"]["frac"] > 0
+
+
 def test_dump_outputs_repeat_bit_for_bit(tmp_path):
     """bench.py --dump-outputs: two runs with the same arguments write the same arrays (the flag implies the deterministic step)."""
     import numpy as np
