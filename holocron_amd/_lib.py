@@ -216,6 +216,8 @@ SIGNATURES = {
     "hc_conv_pointwise": (c_int32, [C.POINTER(ConvDesc), c_void_p]),
     "hc_conv_small": (c_int32, [C.POINTER(ConvSmallDesc), c_void_p]),
     "hc_conv_small_supported": (c_int32, [C.POINTER(ConvSmallDesc)]),
+    "hc_conv_rows_fused_bwd_supported": (c_int32, [C.POINTER(ConvSmallDesc)]),
+    "hc_conv_rows_fused_bwd": (c_int32, [C.POINTER(ConvSmallDesc), c_void_p, c_void_p, c_int32] + [c_void_p] * 8),
     "hc_conv_s2_supported": (c_int32, [C.POINTER(ConvS2Desc)]),
     "hc_conv_s2_fwd": (c_int32, [C.POINTER(ConvS2Desc), c_void_p]),
     "hc_conv_s2_dgrad_supported": (c_int32, [C.POINTER(ConvS2DgradDesc)]),

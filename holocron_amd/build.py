@@ -45,7 +45,7 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-r
 
 
 def _deps():
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(ROOT, "..", "include", "holocron_hip.h")]
+    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "rep_ew.h"), os.path.join(ROOT, "..", "include", "holocron_hip.h")]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -3,6 +3,9 @@
 // Same contract as the other hc_conv_small kernels (hc_conv_small_desc):
 //   mode 0 (forward) : out3 = W3 (*) A, out1 = W1 . A (+ BN statistics of both)
 //   mode 1 (dgrad)   : out3 = W3 (*) A + W1 . B + resid      (A = dy3, B = dy1, weights flipped by the packer)
+// and, through its own entry point (hc_conv_rows_fused_bwd),
+//   mode 2 (dgrad from the block's incoming gradient): mode 1 with A, B and resid (dy3, dy1, dx_id of hc_rep_bwd_apply_z) formed from
+//                      (g, y3, y1, x) in the unit's prologue instead of DMA'd from HBM; the three are still written out.
 //
 // Why another kernel: the image-resident kernel (conv_resident.hip) runs one 8-wave workgroup per image in lockstep - stage the
 // window, 30 barrier-separated k-steps, store - and a knock-out timing (HC_CRS_DBG) put 21 of its 59 us into the exposed window
@@ -33,6 +36,7 @@
 // (920 TFLOP/s; image-resident kernel 62.7), data gradient 44 us (62.7); 96 @ 28x28 46 / 56 us (gather-conv: 3 launches, 195 us).
 #include <type_traits>
 #include "common.h"
+#include "rep_ew.h"
 #include "../../include/holocron_hip.h"
 
 namespace crw {
@@ -43,6 +47,13 @@ struct Args {
     hc_conv_small_desc d;
     int reps;          // statistics replicas
     int delay;         // start-up delay of the second team (s_sleep rounds): de-phases the two teams of a workgroup
+};
+// mode 2: the operands of hc_rep_bwd_apply_z; d.srcB / d.resid are the dy1 / dx_id this kernel writes and reads back
+struct FusedArgs : Args {
+    const void *g, *y3, *y1, *x;
+    const float *coef, *bcoef;      // [4][C] of hc_rep_bn_finalize, [9][C] of hc_rep_bn_bwd_finalize
+    void* dy3;
+    int act;
 };
 
 // W > 0: the map width is a compile-time constant (the two RepVGG-A0 stages at 224 x 224: their codegen is what rounds 2-3 tuned).
@@ -74,6 +85,10 @@ __device__ __forceinline__ void dma16s(const u32x4 rsrc, unsigned lds_off, unsig
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_off), "v"(voff), "s"(rsrc), "s"(soff)
                  : "memory");
 }
+// the same DMA past the vector L1 (sc1): for bytes that this kernel has stored itself
+__device__ __forceinline__ void dma16_sc1(const u32x4 rsrc, unsigned lds_off, unsigned voff) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen sc1 lds" ::"s"(lds_off), "v"(voff), "s"(rsrc) : "memory");
+}
 __device__ __forceinline__ u32x4 uniform_rsrc(const void* p, unsigned bytes) {
     const unsigned long long v = reinterpret_cast<unsigned long long>(p);
     u32x4 r;
@@ -98,9 +113,9 @@ __device__ __forceinline__ float row16_sum(float v) {
 }
 
 // DBG (timing knock-outs, HC_CRW_DBG; results are wrong): 1 no MFMA, 2 no fragment reads, 4 no weight DMA, 8 no window staging,
-// 16 no epilogue
+// 16 no epilogue, 32 no fused prologue (mode 2: no loads of g / y3 / y1 / x, no branch gradients, nothing written to the window)
 template <int C, int W, int MODE, int DBG>
-__global__ __launch_bounds__(NT, 1) void conv_rows_kernel(const Args a) {
+__global__ __launch_bounds__(NT, 1) void conv_rows_kernel(const std::conditional_t<MODE == 2, FusedArgs, Args> a) {
     using G = Geo<C, W>;
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     const hc_conv_small_desc& d = a.d;
@@ -135,7 +150,7 @@ __global__ __launch_bounds__(NT, 1) void conv_rows_kernel(const Args a) {
 
     const unsigned act_bytes = (unsigned)d.N * H * Wr * C * 2u;
     const u32x4 rsA = uniform_rsrc(d.srcA, act_bytes);
-    const u32x4 rsB = uniform_rsrc(MODE == 1 ? d.srcB : d.srcA, act_bytes);
+    const u32x4 rsB = uniform_rsrc(MODE != 0 ? d.srcB : d.srcA, act_bytes);
     const __amdgpu_buffer_rsrc_t rsw = make_rsrc(d.w3, (unsigned)(S * C * 64));
 
     // ---- weights: straight from L2 into registers, two steps ahead (every wave owns its 48 output channels, nothing to share through
@@ -157,6 +172,7 @@ __global__ __launch_bounds__(NT, 1) void conv_rows_kernel(const Args a) {
 
     // ---- window DMA by the four waves of a team: slot (r, x) = r WW + x of a unit holds input pixel (row0 - 1 + r, x - 1); chunk PSC - 1
     // of a slot, the halo and the rounded tail are zero-filled through out-of-range offsets.  j0 .. j1: which 1 KB pieces.
+    // (mode 2 stages only what the team itself stored a moment ago: past the vector L1)
     auto stage_window = [&](const u32x4 rs, int row0, int j0, int j1) __attribute__((always_inline)) {
         if (DBG & 8) return;
         const unsigned img = (unsigned)n * (unsigned)(H * Wr * C * 2);
@@ -167,7 +183,100 @@ __global__ __launch_bounds__(NT, 1) void conv_rows_kernel(const Args a) {
             const int ih = row0 - 1 + r;
             const bool ok = c < G::PSC - 1 && slot < G::NSLOT && x >= 1 && (W > 0 || x <= Wr) && ih >= 0 && ih < H;
             const unsigned off = img + (unsigned)((ih * Wr + x - 1) * C * 2 + c * 16);
-            hc_dma16(rs, lds0 + (unsigned)(region + j * 1024), ok ? off : HC_OOB);
+            if (MODE == 2) dma16_sc1(rs, lds0 + (unsigned)(region + j * 1024), ok ? off : HC_OOB);
+            else hc_dma16(rs, lds0 + (unsigned)(region + j * 1024), ok ? off : HC_OOB);
+        }
+    };
+
+    // ---- mode 2: the unit's window of dy3 is FORMED here instead of staged.  The team's lanes sweep the 9 window rows of (g, y3, y1, x)
+    // pixel-major: lane tt keeps the 8-channel chunk tt % (C / 8) for all its pixels (its 13 x 8 coefficients sit in registers, as in
+    // the elementwise kernels of rep_bn.hip) and takes pixel tt / (C / 8) of every sweep of 256 / (C / 8) pixels; two batches of BATCH sweeps
+    // (4 BATCH 16-byte loads per lane each) are in flight, the second one requested before the first is used.  dy3 (bf16) goes to the window slot, and for the unit's own 7 rows
+    // also to HBM (the weight gradients read it) next to dy1 and dx_id, which this kernel reads back after the ninth tap / in the
+    // epilogue.  The halo rows are computed by both neighbouring teams, stored by their owner only.  Everything stage_window() zero-fills
+    // (halo column, rows outside the image, pad chunk, tail) is zeroed by the first loop: the two write disjoint bytes.
+    auto fused_prologue = [&](int row0) __attribute__((always_inline)) {
+        if constexpr (MODE == 2) {
+            if (DBG & 32) return;
+            constexpr int CG = C / 8, PPS = 256 / CG, BATCH = 2;
+            for (int j = w4; j < G::NDMA; j += 4) {
+                const int J = j * 64 + lane;
+                const int slot = J / G::PSC, c = J - slot * G::PSC;
+                const int r = slot / WW, x = slot - r * WW;
+                const int ih = row0 - 1 + r;
+                const bool ok = c < G::PSC - 1 && slot < G::NSLOT && x >= 1 && (W > 0 || x <= Wr) && ih >= 0 && ih < H;
+                if (!ok) *reinterpret_cast<u32x4*>(smem + region + J * 16) = u32x4{0u, 0u, 0u, 0u};
+            }
+            const int tt = w4 * 64 + lane;
+            const int pl = tt / CG, chunk = tt - pl * CG;
+            const bool active = pl < PPS;
+            int c0 = chunk * 8;
+            asm volatile("" : "+v"(c0));          // re-read per unit: hoisted out of the unit loop the 104 coefficients would live across the k-loop
+            float a3[8], a1[8], a0[8], sh[8], A3[8], B3[8], C3[8], A1[8], B1[8], C1[8], A0[8], B0[8], C0[8];
+            load8f(a.coef + c0, a3); load8f(a.coef + C + c0, a1); load8f(a.coef + 2 * C + c0, a0); load8f(a.coef + 3 * C + c0, sh);
+            load8f(a.bcoef + 0 * C + c0, A3); load8f(a.bcoef + 1 * C + c0, B3); load8f(a.bcoef + 2 * C + c0, C3);
+            load8f(a.bcoef + 3 * C + c0, A1); load8f(a.bcoef + 4 * C + c0, B1); load8f(a.bcoef + 5 * C + c0, C1);
+            load8f(a.bcoef + 6 * C + c0, A0); load8f(a.bcoef + 7 * C + c0, B0); load8f(a.bcoef + 8 * C + c0, C0);
+            const __amdgpu_buffer_rsrc_t rg = make_rsrc(a.g, act_bytes), r3 = make_rsrc(a.y3, act_bytes), r1 = make_rsrc(a.y1, act_bytes),
+                                         rx = make_rsrc(a.x, act_bytes), rd3 = make_rsrc(a.dy3, act_bytes),
+                                         rd1 = make_rsrc(d.srcB, act_bytes), rd0 = make_rsrc(d.resid, act_bytes);
+            const int HW = H * Wr, NP = (UR + 2) * Wr;
+            const int gp0 = (row0 - 1) * Wr;                 // window pixel p is image pixel gp0 + p (rows are contiguous in NHWC)
+            const int act = a.act;
+            struct Batch { u32x4 vg[BATCH], v3[BATCH], v1[BATCH], vx[BATCH]; unsigned off[BATCH]; };
+            auto request = [&](Batch& q, int pb) __attribute__((always_inline)) {
+#pragma unroll
+                for (int b = 0; b < BATCH; ++b) {
+                    const int p = pb + b * PPS, gp = gp0 + p;
+                    const bool ok = active && p < NP && gp >= 0 && gp < HW;
+                    q.off[b] = ok ? (unsigned)(((n * HW + gp) * CG + chunk) * 16) : HC_OOB;
+                    q.vg[b] = buf_load16(rg, q.off[b]);
+                    q.v3[b] = buf_load16(r3, q.off[b]);
+                    q.v1[b] = buf_load16(r1, q.off[b]);
+                    q.vx[b] = buf_load16(rx, q.off[b]);
+                }
+            };
+            auto finish = [&](const Batch& q, int pb) __attribute__((always_inline)) {
+#pragma unroll
+                for (int b = 0; b < BATCH; ++b) {
+                    const int p = pb + b * PPS;
+                    float fg[8], f3[8], f1[8], f0[8], o3[8], o1[8], o0[8];
+                    unpack8(q.vg[b], fg); unpack8(q.v3[b], f3); unpack8(q.v1[b], f1); unpack8(q.vx[b], f0);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const float fo = act == 1 ? rep_preact<true>(a3[i], f3[i], a1[i], f1[i], a0[i], f0[i], sh[i]) : 1.f;
+                        const float dz = rep_bwd_dz(fo, fg[i]);
+                        o3[i] = rep_bwd_branch(A3[i], dz, B3[i], f3[i], C3[i]);
+                        o1[i] = rep_bwd_branch(A1[i], dz, B1[i], f1[i], C1[i]);
+                        o0[i] = rep_bwd_branch(A0[i], dz, B0[i], f0[i], C0[i]);
+                    }
+                    const u32x4 p3 = pack8(o3);
+                    if (q.off[b] != HC_OOB) {
+                        const int r = p / Wr, x = p - r * Wr;
+                        *reinterpret_cast<u32x4*>(smem + region + (r * WW + x + 1) * PS + chunk * 16) = p3;
+                    }
+                    const unsigned so = (p >= Wr && p < (UR + 1) * Wr) ? q.off[b] : HC_OOB;    // the unit's own rows (out of range: dropped)
+                    __builtin_amdgcn_raw_buffer_store_b128(p3, rd3, so, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(pack8(o1), rd1, so, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(pack8(o0), rd0, so, 0, 0);
+                }
+            };
+            // two batches in a ring: the loads of the next batch are requested before the current one is consumed (a batch past the
+            // window asks for nothing: all its offsets are out of range)
+            constexpr int STEP = BATCH * PPS;
+            Batch q0, q1;
+            request(q0, pl);
+#pragma nounroll
+            for (int pb = pl; pb < NP + pl; pb += 2 * STEP) {
+                request(q1, pb + STEP);
+                __builtin_amdgcn_sched_barrier(0);
+                finish(q0, pb);
+                __builtin_amdgcn_sched_barrier(0);
+                request(q0, pb + 2 * STEP);
+                __builtin_amdgcn_sched_barrier(0);
+                finish(q1, pb + STEP);
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
     };
 
@@ -259,12 +368,15 @@ __global__ __launch_bounds__(NT, 1) void conv_rows_kernel(const Args a) {
                         st[1][f * 4 + e] += x * x;
                     }
                 }
-                if (MODE == 1 && rp != nullptr && ok) {
-                    const u32x2 rv = *reinterpret_cast<const u32x2*>(rp + cofs);
+                if (MODE != 0 && rp != nullptr && ok) {
+                    // (mode 2: dx_id was stored by this team's prologue - read it past the vector L1)
+                    const u32x2 rv = MODE == 2 ? __builtin_bit_cast(u32x2, __hip_atomic_load(reinterpret_cast<const unsigned long long*>(rp + cofs),
+                                                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                                               : *reinterpret_cast<const u32x2*>(rp + cofs);
                     v[0] += bf16lo(rv[0]); v[1] += bf16hi(rv[0]); v[2] += bf16lo(rv[1]); v[3] += bf16hi(rv[1]);
                 }
                 pk[f] = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
-                if (MODE == 1 && ok) *reinterpret_cast<u32x2*>(op + cofs) = pk[f];
+                if (MODE != 0 && ok) *reinterpret_cast<u32x2*>(op + cofs) = pk[f];
             }
             if (MODE == 0 && ok) {
                 *reinterpret_cast<u32x4*>(op) = u32x4{pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
@@ -293,8 +405,9 @@ __global__ __launch_bounds__(NT, 1) void conv_rows_kernel(const Args a) {
     for (int u = team; u < UPI; u += 2) {
         const int row0 = u * UR;
         if (u >= 2) team_sync();                            // every wave of the team is done reading the previous unit's window
-        stage_window(rsA, row0, 0, G::NDMA);
-        team_sync();                                        // the window has landed
+        if (MODE == 2) fused_prologue(row0);
+        else stage_window(rsA, row0, 0, G::NDMA);
+        team_sync();                                        // the window has landed (mode 2: and the team's dy1 / dx_id stores are drained)
         load_a(0, 0);
         load_a(1, 1);
         zero_acc();
@@ -346,7 +459,7 @@ bool shape_ok(const hc_conv_small_desc& d) {
 }
 
 template <int C, int W, int MODE, int DBG>
-void launch1(const Args& a, hipStream_t st) {
+void launch1(const std::conditional_t<MODE == 2, FusedArgs, Args>& a, hipStream_t st) {
     auto kern = conv_rows_kernel<C, W, MODE, DBG>;
     constexpr int smem = Geo<C, W>::SMEM;
     static bool attr_set = false;
@@ -365,6 +478,18 @@ void launch(const Args& a, hipStream_t st) {
     switch (dbg) {
         CRW_CASE(1) CRW_CASE(2) CRW_CASE(3) CRW_CASE(4) CRW_CASE(7) CRW_CASE(8) CRW_CASE(16) CRW_CASE(24) CRW_CASE(31)
         default: if (dg) launch1<C, W, 1, 0>(a, st); else launch1<C, W, 0, 0>(a, st); break;
+    }
+#undef CRW_CASE
+}
+
+// mode 2; the knock-outs of the other modes plus 32 (no fused prologue)
+template <int C, int W>
+void launch_fused(const FusedArgs& a, hipStream_t st) {
+    static const int dbg = getenv("HC_CRW_DBG") ? atoi(getenv("HC_CRW_DBG")) : 0;
+#define CRW_CASE(k) case k: launch1<C, W, 2, k>(a, st); break;
+    switch (dbg) {
+        CRW_CASE(1) CRW_CASE(2) CRW_CASE(3) CRW_CASE(4) CRW_CASE(7) CRW_CASE(8) CRW_CASE(16) CRW_CASE(24) CRW_CASE(31) CRW_CASE(32)
+        default: launch1<C, W, 2, 0>(a, st); break;
     }
 #undef CRW_CASE
 }
@@ -398,5 +523,35 @@ int hc_conv_rows_launch(const hc_conv_small_desc& d, hipStream_t st) {
     else if (crw::shape_ok<96, 28>(d)) crw::launch<96, 28>(a, st);
     else if (d.C == 192) { if (dg) crw::launch1<192, 0, 1, 0>(a, st); else crw::launch1<192, 0, 0, 0>(a, st); }
     else { if (dg) crw::launch1<96, 0, 1, 0>(a, st); else crw::launch1<96, 0, 0, 0>(a, st); }
+    return hc_launch_status();
+}
+
+// RepBlock data gradient straight from the block's incoming gradient (mode 2): d as for the data gradient of hc_conv_small with
+// HC_CONV_SMALL_ROWS_IMAGE | 1 (w3 = the mode-4 weight image, out3 = dx; srcA / srcB / resid are ignored), the rest as for
+// hc_rep_bwd_apply_z with an identity branch.
+extern "C" int hc_conv_rows_fused_bwd_supported(const hc_conv_small_desc* dp) {
+    return dp != nullptr && dp->mode == (HC_CONV_SMALL_ROWS_IMAGE | 1) && hc_conv_rows_supported(*dp) ? 1 : 0;
+}
+extern "C" int hc_conv_rows_fused_bwd(const hc_conv_small_desc* dp, const void* g, const float* coef, int32_t act, const void* y3,
+                                      const void* y1, const void* x, const float* bcoef, void* dy3, void* dy1, void* dxid,
+                                      hc_stream_t stream) {
+    if (!hc_conv_rows_fused_bwd_supported(dp)) return HC_ERR_ARG;
+    if (dp->w3 == nullptr || dp->out3 == nullptr || g == nullptr || coef == nullptr || y3 == nullptr || y1 == nullptr || x == nullptr ||
+        bcoef == nullptr || dy3 == nullptr || dy1 == nullptr || dxid == nullptr || (act != 0 && act != 1))
+        return HC_ERR_ARG;
+    const hc_conv_small_desc& d = *dp;
+    hipStream_t st = (hipStream_t)stream;
+    crw::FusedArgs a;
+    a.d = d;
+    a.d.srcA = dy3;
+    a.d.srcB = dy1;
+    a.d.resid = dxid;
+    a.reps = hc_get_stat_replicas();
+    a.delay = 0;
+    a.g = g; a.y3 = y3; a.y1 = y1; a.x = x; a.coef = coef; a.bcoef = bcoef; a.dy3 = dy3; a.act = act;
+    if (crw::shape_ok<192, 14>(d)) crw::launch_fused<192, 14>(a, st);
+    else if (crw::shape_ok<96, 28>(d)) crw::launch_fused<96, 28>(a, st);
+    else if (d.C == 192) crw::launch1<192, 0, 2, 0>(a, st);
+    else crw::launch1<96, 0, 2, 0>(a, st);
     return hc_launch_status();
 }

@@ -6,6 +6,7 @@
 // iteration and the launch is sized so that a thread's channel group never changes, which
 // keeps the per-channel coefficients in registers.
 #include "common.h"
+#include "rep_ew.h"
 #include "../../include/holocron_hip.h"
 #include <stdlib.h>
 
@@ -34,22 +35,6 @@ inline int ew_blocks(long nchunks, int cg, int cpt_default = 8) {
     if (want < 1) want = 1;
     long k = (want + unit - 1) / unit;
     return (int)(k * unit);
-}
-
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { f[2 * i] = bf16lo(v[i]); f[2 * i + 1] = bf16hi(v[i]); }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
-    u32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = pack_bf16x2(f[2 * i], f[2 * i + 1]);
-    return v;
-}
-__device__ __forceinline__ void load8f(const float* p, float (&f)[8]) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { f[i] = a[i]; f[4 + i] = b[i]; }
 }
 
 // Streaming accesses of the elementwise passes.  NT: tensors far larger than the 256 MB last-level cache (the 112x112 and 56x56
@@ -210,15 +195,7 @@ __global__ __launch_bounds__(256) void rep_bn_finalize_kernel(const hc_rep_bn_de
 }
 
 // ---------------------------------------------------------------- forward apply
-// pre-activation of the fused block output.  ONE explicit fma chain used by the forward apply and by the backward kernels that
-// recompute the ReLU mask from it (hc_rep_bwd_*_z): the same inputs give the same bits, so (z > 0) there IS (out > 0) here
-// (out = bf16(relu(z)) > 0 exactly when z > 0: a positive fp32 never rounds to a bf16 zero above 2^-134).
-template <bool HAS_ID>
-__device__ __forceinline__ float rep_preact(float a3, float f3, float a1, float f1, float a0, float f0, float sh) {
-    float z = __builtin_fmaf(a1, f1, sh);
-    if (HAS_ID) z = __builtin_fmaf(a0, f0, z);
-    return __builtin_fmaf(a3, f3, z);
-}
+// (pre-activation: rep_preact, rep_ew.h)
 template <bool HAS_ID, bool STATS, bool NT>
 __global__ __launch_bounds__(EW_THREADS) void rep_apply_kernel(const u32x4* __restrict__ y3, const u32x4* __restrict__ y1,
                                                                const u32x4* __restrict__ x, const float* __restrict__ coef,
@@ -440,10 +417,10 @@ __global__ __launch_bounds__(EW_THREADS) void rep_bwd_apply_kernel(const u32x4* 
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             if (ZMASK) fo[i] = act == 1 ? rep_preact<HAS_ID>(a3[i], f3[i], a1[i], f1[i], HAS_ID ? a0[i] : 0.f, HAS_ID ? f0[i] : 0.f, sh[i]) : 1.f;
-            const float dz = fo[i] > 0.f ? fg[i] : 0.f;
-            o3[i] = __builtin_fmaf(A3[i], dz, __builtin_fmaf(B3[i], f3[i], C3[i]));   // explicit chains: every instantiation rounds alike
-            o1[i] = __builtin_fmaf(A1[i], dz, __builtin_fmaf(B1[i], f1[i], C1[i]));
-            if (HAS_ID) o0[i] = __builtin_fmaf(A0[i], dz, __builtin_fmaf(B0[i], f0[i], C0[i]));
+            const float dz = rep_bwd_dz(fo[i], fg[i]);
+            o3[i] = rep_bwd_branch(A3[i], dz, B3[i], f3[i], C3[i]);   // explicit chains (rep_ew.h): every kernel that forms them rounds alike
+            o1[i] = rep_bwd_branch(A1[i], dz, B1[i], f1[i], C1[i]);
+            if (HAS_ID) o0[i] = rep_bwd_branch(A0[i], dz, B0[i], f0[i], C0[i]);
         }
         st16<NT>(dy3 + q, pack8(o3));
         st16<NT>(dy1 + q, pack8(o1));

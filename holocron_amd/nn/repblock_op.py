@@ -11,6 +11,7 @@ Kernel sequence (DESIGN.md "RepBlock step"):
   backward: rep_bwd_reduce (sum dz, dz*y3, dz*y1, dz*x) ; bn_bwd_finalize ; rep_bwd_apply
             (dy3, dy1, dx_identity) ; dual-source dgrad (3x3 + 1x1 in one accumulator, + dx_id) ;
             wgrad 3x3 ; wgrad 1x1
+            (identity blocks of the 192- / 96-channel stages: rep_bwd_apply and the dgrad are ONE launch, block_dgrad_fused)
 """
 import ctypes as C
 
@@ -23,6 +24,9 @@ from .._lib import ConvS2Desc, ConvS2DgradDesc, PackItem, RepBnBwdDesc, RepBnDes
 from ..ops import conv as cv
 
 STEM_KPAD = 32
+# HC_REP_FUSED_BWD=0 (read once, here): identity blocks on the 192- / 96-channel row-unit kernel go back to the two launches
+# hc_rep_bwd_apply_z + data gradient instead of hc_conv_rows_fused_bwd (A/B; both give the same bits)
+FUSED_BWD = os.environ.get("HC_REP_FUSED_BWD", "1") != "0"
 
 
 class ZeroPool:
@@ -402,6 +406,30 @@ def block_dgrad(st, dy3, dy1, dxid, w3, w1, geom):
     return dx
 
 
+def fused_dgrad_desc(st, geom):
+    """The data-gradient descriptor of this geometry when hc_conv_rows_fused_bwd takes it (stride 1, Cin == Cout on the 192- /
+    96-channel row-unit kernel), else None."""
+    N, Cin, H, W, Cout = geom
+    sdg = st.descs(N, Cin, H, W, Cout)[4]
+    if sdg is None or not st.rows_image[1] or Cin != Cout or not _lib.load().hc_conv_rows_fused_bwd_supported(C.byref(sdg)):
+        return None
+    return sdg
+
+
+def block_dgrad_fused(st, sdg, g, coef, act, y3, y1, x, bcoef, w3, w1, bufs=None):
+    """(dy3, dy1, dx_id, dx) of an identity block in one launch: hc_rep_bwd_apply_z formed inside the row-unit data gradient.
+    ``bufs``: the four output tensors, when the caller brings its own."""
+    wpd = st.ensure_packed(w3, w1)[2]
+    dy3, dy1, dxid, dx = bufs if bufs is not None else (torch.empty_like(y3), torch.empty_like(y1), torch.empty_like(x), torch.empty_like(x))
+    sdg.srcA, sdg.srcB, sdg.resid, sdg.w3, sdg.w1, sdg.out3, sdg.out1, sdg.stats3, sdg.stats1 = None, None, None, ptr(wpd), None, ptr(dx), None, None, None
+    tb = x.numel() * 2.0
+    # one entry, under the conv family: the data gradient's FLOPs, four reads (g, y3, y1, x) and four writes (dy3, dy1, dx_id, dx)
+    with cv.profiled("conv_rows", 2.0 * sdg.N * sdg.H * sdg.W * sdg.Cout * 10 * sdg.C, 8 * tb):
+        check(_lib.load().hc_conv_rows_fused_bwd(C.byref(sdg), ptr(g), ptr(coef), act, ptr(y3), ptr(y1), ptr(x), ptr(bcoef), ptr(dy3),
+                                                 ptr(dy1), ptr(dxid), stream()), "hc_conv_rows_fused_bwd")
+    return dy3, dy1, dxid, dx
+
+
 def block_wgrad(st, src, dy3, dy1, w3, w1, geom, stem_cin=None, defer=False):
     """(dW3, dW1) fp32 OIHW from the block input ``src`` and the two branch gradients.  ``defer`` (only inside an autograd
     backward pass): the fused kernel's launch may be queued and grouped with same-shaped blocks (ops/conv.py _RepWgradQueue)."""
@@ -592,19 +620,22 @@ class RepBlockFn(torch.autograd.Function):
         with cv.profiled("bn_finalize", 0.0, 0.0):
             check(lib.hc_rep_bn_bwd_finalize(C.byref(d), stream()), "hc_rep_bn_bwd_finalize")
 
-        dy3 = torch.empty_like(y3)
-        dy1 = torch.empty_like(y1)
-        dxid = torch.empty_like(src) if st.identity else None
-        with cv.profiled("bn_elementwise", 0.0, tb * (7 if st.identity else 5)):      # reads g, y3, y1 [, x], writes dy3, dy1 [, dx_id]
-            check(lib.hc_rep_bwd_apply_z(ptr(g), ptr(coef), act, ptr(y3), ptr(y1), ptr(xid), ptr(bcoef), ptr(dy3), ptr(dy1),
-                                         ptr(dxid), npix, Cout, stream()), "hc_rep_bwd_apply_z")
-
         dx = None
         geom = (N, Cin, H, W, Cout)
-        if ctx.needs_input_grad[0]:
-            if ctx.stem:
-                raise NotImplementedError("input gradient of the im2col stem path")
-            dx = block_dgrad(st, dy3, dy1, dxid, w3, w1, geom)
+        fdg = fused_dgrad_desc(st, geom) if (FUSED_BWD and st.identity and ctx.needs_input_grad[0] and not ctx.stem) else None
+        if fdg is not None:
+            dy3, dy1, dxid, dx = block_dgrad_fused(st, fdg, g, coef, act, y3, y1, src, bcoef, w3, w1)
+        else:
+            dy3 = torch.empty_like(y3)
+            dy1 = torch.empty_like(y1)
+            dxid = torch.empty_like(src) if st.identity else None
+            with cv.profiled("bn_elementwise", 0.0, tb * (7 if st.identity else 5)):      # reads g, y3, y1 [, x], writes dy3, dy1 [, dx_id]
+                check(lib.hc_rep_bwd_apply_z(ptr(g), ptr(coef), act, ptr(y3), ptr(y1), ptr(xid), ptr(bcoef), ptr(dy3), ptr(dy1),
+                                             ptr(dxid), npix, Cout, stream()), "hc_rep_bwd_apply_z")
+            if ctx.needs_input_grad[0]:
+                if ctx.stem:
+                    raise NotImplementedError("input gradient of the im2col stem path")
+                dx = block_dgrad(st, dy3, dy1, dxid, w3, w1, geom)
 
         with cv.side_stream_for_wgrad((w3, w1), (src, dy3, dy1)) as side:
             dw3, dw1 = block_wgrad(st, src, dy3, dy1, w3, w1, geom, Cin if ctx.stem else None, defer=True)

@@ -128,6 +128,15 @@ typedef struct {
 } hc_conv_small_desc;
 int hc_conv_small(const hc_conv_small_desc* d, hc_stream_t stream);
 int hc_conv_small_supported(const hc_conv_small_desc* d);
+/* RepBlock data gradient of the row-unit kernel for 192 / 96 channels (conv_rows.hip) straight from the block's incoming gradient:
+ * hc_rep_bwd_apply_z with an identity branch and the data gradient of hc_conv_small (mode HC_CONV_SMALL_ROWS_IMAGE | 1) in ONE launch.
+ * Every unit of 7 rows forms dy3 / dy1 / dx_id of its 9-row window from (g, y3, y1, x, coef, bcoef) in its prologue - the same fma
+ * chains, the same bits as hc_rep_bwd_apply_z - keeps dy3 in LDS for the nine taps and writes all three out for its own rows (the
+ * weight gradients read dy3 / dy1).  d: N, H, W, C = Cout, mode, w3 (weight image of pack mode 4) and out3 (dx); its srcA / srcB / resid
+ * are ignored.  _supported: the shapes of conv_rows.hip (192 channels up to 16 pixels wide, 96 up to 32). */
+int hc_conv_rows_fused_bwd_supported(const hc_conv_small_desc* d);
+int hc_conv_rows_fused_bwd(const hc_conv_small_desc* d, const void* g, const float* coef, int32_t act, const void* y3, const void* y1,
+                           const void* x, const float* bcoef, void* dy3, void* dy1, void* dxid, hc_stream_t stream);
 
 /* Stride-2 RepBlock forward of the HBM-bound front layers (csrc/conv_s2.hip): y3 = conv3x3(x, stride 2, pad 1),
  * y1 = conv1x1(x, stride 2) and the per-channel sum / sum of squares of both fp32 results - the two nn.Conv2d of a stride-2
